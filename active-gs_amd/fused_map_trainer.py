@@ -399,7 +399,7 @@ class FusedMapTrainer(GaussianMapTrainer):
                 """Run fn(slot, b, stream_handle) for this rank's views, round-robin over S streams that
                 first wait for the main stream and that the main stream then waits for.  The kernels
                 are enqueued through the C ABI with the raw stream handle (no torch stream switch)."""
-                if S == 1:
+                if S == 1 or torch.cuda.is_current_stream_capturing():     # (recording: one stream, see api.forward_many)
                     for slot, b in enumerate(mine):
                         fn(slot, b, main_h)
                     return

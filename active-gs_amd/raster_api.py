@@ -413,7 +413,9 @@ def forward_many(cams: Sequence[Camera], g: Gaussians, states: Sequence[ForwardS
         raise ValueError("one ForwardState per camera")
     for name in ("means3D", "scales", "rotations", "opacities", "colors", "confidences"):
         _require_cuda(getattr(g, name), name)
-    if pool is None or len(cams) < 2:
+    # While a graph is being recorded the views stay on the capturing stream: the HIP runtime this package runs on
+    # crashes in hipGraphLaunch on graphs whose capture forked onto other streams (parallel branches).
+    if pool is None or len(cams) < 2 or torch.cuda.is_current_stream_capturing():
         for cam, st in zip(cams, states):
             forward(cam, g, st, checked=True)
         return

@@ -294,8 +294,8 @@ class SurfelTrainer:
         """Streams the views of a multi-view step are spread over (VIEW_STREAMS > 1): a view's four launches depend
         on nothing another view of the step produces until the per-Gaussian backward joins them."""
         k = min(int(self.VIEW_STREAMS), views)
-        if k <= 1:
-            return []
+        if k <= 1 or torch.cuda.is_current_stream_capturing():
+            return []      # a step being recorded stays on the capturing stream: see api.forward_many
         while len(self._lanes) < k:
             self._lanes.append(torch.cuda.Stream())
         return self._lanes[:k]

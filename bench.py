@@ -610,6 +610,44 @@ def cpu_baseline(raw_cpu, cam_cpu, d_img_cpu, gpu_check, budget_s=15.0, max_thre
     return base, parity
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, trainer, st, raw_cpu, run_steps, prime=None):
+    """``--dump-outputs``: what one step of the timed path computes, from inputs that are the same in every run.  The
+    parameters the timed region's last step started from are not: the clock warm-up runs for a fixed time, and the blend
+    backward sums its gradient records with atomics, whose order - and so the last bit of a sum - changes from run to run
+    and is carried into every later step (Adam divides by the gradients' own size).  So the trainer is put back at the
+    seeded scene with a fresh optimiser and ONE step of the same replay runs: its images are bit-identical from run to
+    run, its updated parameters differ by the rounding of those sums.  What a caller of the step receives - the updated
+    parameters and the images the step rendered - is written as ``<name>.npy`` (float32).  Every rank takes the step
+    (collectives); the caller writes on rank 0 only.  ``prime``: a software-pipelined timed path's eager step (what
+    ``capture`` itself takes to start the pipeline), run instead of a replay.  -> {name: shape}"""
+    import numpy as np
+    trainer.reset_optimizer()
+    with torch.no_grad():
+        for k, v in trainer.raw.items():
+            v.copy_(raw_cpu[k].to(v.device))
+        for img in (st.rgb, st.normal, st.depth, st.opacity, st.confidence):
+            img.zero_()
+    if prime is not None:
+        prime()         # (software-pipelined: this eager step from the seed IS the step; a replay would start after it)
+    else:
+        run_steps(1)
+    torch.cuda.synchronize()
+    arrays = {f"param_{k}": trainer.raw[k] for k in ("means", "scales", "rotations", "opacities", "harmonics")}
+    arrays.update({f"image_{k}": getattr(st, k) for k in ("rgb", "normal", "depth", "opacity", "confidence")})
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    if outdir is not None:
+        os.makedirs(outdir, exist_ok=True)
+        for k, a in arrays.items():
+            np.save(os.path.join(outdir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def launch_ranks(args) -> int:
     """``--gpus N`` without a launcher: start N ranks (one per GPU) as a child job and relay rank 0's JSON line.
     Runs before anything in this process has touched the GPU (no GPU state to share, no re-exec).  On failure the
@@ -680,9 +718,15 @@ def main():
     ap.add_argument("--graph-steps", type=int, default=int(os.environ.get("AGS_BENCH_GRAPH_STEPS", "25")),
                     help="optimisation steps recorded per hipGraph (single GPU); K steps = K/this replays")
     ap.add_argument("--check", action="store_true", help="multi-GPU readiness check only (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region: restore the seeded scene and a fresh optimiser, run one step of the timed "
+                         "path and write what it computed (updated parameters, rendered images) as DIR/<name>.npy; the "
+                         "inputs are the same in every run, so two builds can be compared output for output")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "RANK" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args))
 
@@ -910,6 +954,10 @@ def main():
     st = trainer.state_for(H, W, cap)
     info = api.read_status(st)
     refused = trainer.refused_steps() if dist_on else 0      # steps the row exchange refused (segment outgrown)
+    dumped = None
+    if args.dump_outputs:
+        prime = (lambda: trainer.step([cam], grads_fn, cap, next_cam=cam)) if getattr(one_step, "pipelined", False) else None
+        dumped = dump_outputs(args.dump_outputs if rank == 0 else None, trainer, st, raw_cpu, run_steps, prime)
 
     extras = {}
     if not dist_on and not args.eager and not args.no_extras and args.binning == "direct":
@@ -1081,6 +1129,10 @@ def main():
                          "whole_step_GBps": sum(sb.values()) / step_s / 1e9},
         }
         out.update(extras)
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped,
+                                   "what": "one step of the timed path from the seeded scene and a fresh optimiser, run after "
+                                           "the timed region: updated parameters and the images it rendered (float32)"}
         if valu is not None:
             out["roofline_valu"] = valu
         if strong is not None:

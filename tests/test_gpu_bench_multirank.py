@@ -200,3 +200,37 @@ def test_a_hung_rank_ends_the_job_with_stacks_not_a_silent_timeout(agslib):
                        text=True, timeout=400)
     assert r.returncode != 0
     assert "Timeout" in r.stderr and "exited with code" in r.stderr, r.stderr[-2000:]
+
+
+def test_bench_dump_outputs_are_the_same_for_the_same_arguments(agslib, tmp_path):
+    """``bench.py --dump-outputs DIR``: one step of the timed path from the seeded scene (updated parameters, rendered
+    images) as float32 .npy files within 64 MB - two runs with different --warmup (so a different number of steps before
+    the timed region) write the same arrays: the images bit for bit, the parameters up to the rounding of the blend
+    backward's atomic sums."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    runs = []
+    for warmup in (2, 7):
+        out = tmp_path / f"w{warmup}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", str(warmup),
+                            "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(out)], env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["ms_per_step"] > 0
+        names = sorted(d["dump_outputs"]["arrays"])
+        assert sorted(p.name for p in out.iterdir()) == [n + ".npy" for n in names]
+        arrays = {n: np.load(out / (n + ".npy")) for n in names}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["param_means"].shape == (200_000, 3) and arrays["image_rgb"].shape == (3, 680, 1200)
+        assert np.abs(arrays["image_rgb"]).max() > 0
+        runs.append(arrays)
+    a, b = runs
+    for n in a:
+        if n.startswith("image_"):
+            assert np.array_equal(a[n], b[n]), n
+        else:
+            assert np.allclose(a[n], b[n], rtol=1e-5, atol=1e-7), (n, float(np.abs(a[n].astype(np.float64) - b[n]).max()))
