@@ -1,7 +1,7 @@
 // extern "C" entry points of libags_raster.so (include/ags_raster.h).
 #include "ags_internal.h"
 
-#define AGS_VERSION 102   // 102: ags_forward_batch_loss, AGS_BWD_BF16X3
+#define AGS_VERSION 103   // 103: ags_facade_post_backward_batch; 102: ags_forward_batch_loss, AGS_BWD_BF16X3
 
 static int ags_check_launch() { return hipGetLastError() == hipSuccess ? AGS_OK : AGS_E_LAUNCH; }
 
@@ -533,7 +533,19 @@ int ags_facade_post_backward(int32_t h, int32_t w, float tanfov_x, float tanfov_
     if (h <= 0 || w <= 0 || !(tanfov_x > 0.f) || !(tanfov_y > 0.f) || !depth || !opacity) return AGS_E_INVALID;
     if (g_d2n && !d_depth) return AGS_E_INVALID;
     if (d_normal_raw && g_normal && !normal_raw) return AGS_E_INVALID;
-    ags_launch_facade_post_bwd(h, w, tanfov_x, tanfov_y, normal_raw, depth, opacity, g_normal, g_d2n, d_normal_raw, d_depth,
+    ags_launch_facade_post_bwd(1, h, w, tanfov_x, tanfov_y, normal_raw, depth, opacity, g_normal, g_d2n, d_normal_raw, d_depth,
+                               (hipStream_t)stream);
+    return ags_check_launch();
+}
+
+int ags_facade_post_backward_batch(int32_t views, int32_t h, int32_t w, float tanfov_x, float tanfov_y, const float* normal_raw,
+                                   const float* depth, const float* opacity, const float* g_normal, const float* g_d2n,
+                                   float* d_normal_raw, float* d_depth, ags_stream_t stream) {
+    if (views < 1 || views > 65535 || h <= 0 || w <= 0 || !(tanfov_x > 0.f) || !(tanfov_y > 0.f) || !depth || !opacity)
+        return AGS_E_INVALID;
+    if (g_d2n && !d_depth) return AGS_E_INVALID;
+    if (d_normal_raw && g_normal && !normal_raw) return AGS_E_INVALID;
+    ags_launch_facade_post_bwd(views, h, w, tanfov_x, tanfov_y, normal_raw, depth, opacity, g_normal, g_d2n, d_normal_raw, d_depth,
                                (hipStream_t)stream);
     return ags_check_launch();
 }

@@ -362,6 +362,16 @@ __global__ __launch_bounds__(256) void ags_k_facade_post_bwd(AgsPostDev c, const
                                                              float* __restrict__ d_normal_raw, float* __restrict__ d_depth) {
     const int HW = c.H * c.W, p = blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
+    { // a batch of views (ags_facade_post_backward_batch): blockIdx.y = view, images contiguous (views,C,H,W); the view's
+      // offsets in size_t (3 * views * H * W can pass 2^31), the per-pixel arithmetic below is the single view's
+        const size_t v = blockIdx.y;
+        depth += v * HW; opacity += v * HW;
+        if (normal_raw) normal_raw += 3 * v * HW;
+        if (g_normal) g_normal += 3 * v * HW;
+        if (g_d2n) g_d2n += 3 * v * HW;
+        if (d_normal_raw) d_normal_raw += 3 * v * HW;
+        if (d_depth) d_depth += v * HW;
+    }
     const int y = p / c.W, x = p - y * c.W;
     const float mn = opacity[p] > 1e-2f ? 1.f : 0.f;
     if (d_normal_raw) {   // n = normalize(N) * mask
@@ -402,11 +412,11 @@ void ags_launch_facade_post(int views, int h, int w, float tanx, float tany, con
     hipLaunchKernelGGL(ags_k_facade_post, dim3((h * w + 255) / 256, views), dim3(256), 0, s, c, normal_raw, depth, opacity,
                        normal_out, d2n_out);
 }
-void ags_launch_facade_post_bwd(int h, int w, float tanx, float tany, const float* normal_raw, const float* depth,
+void ags_launch_facade_post_bwd(int views, int h, int w, float tanx, float tany, const float* normal_raw, const float* depth,
                                 const float* opacity, const float* g_normal, const float* g_d2n, float* d_normal_raw,
                                 float* d_depth, hipStream_t s) {
     const AgsPostDev c = {h, w, (float)h / (2.0f * tanx), (float)w / (2.0f * tany)};
-    hipLaunchKernelGGL(ags_k_facade_post_bwd, dim3((h * w + 255) / 256), dim3(256), 0, s, c, normal_raw, depth, opacity,
+    hipLaunchKernelGGL(ags_k_facade_post_bwd, dim3((h * w + 255) / 256, views), dim3(256), 0, s, c, normal_raw, depth, opacity,
                        g_normal, g_d2n, d_normal_raw, d_depth);
 }
 

@@ -33,6 +33,7 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
 
+#include <cstring>
 #include <deque>
 #include <map>
 #include <mutex>
@@ -51,6 +52,9 @@ struct Abi {
     decltype(&ags_workspace_init) workspace_init = nullptr;
     decltype(&ags_forward) forward = nullptr;
     decltype(&ags_backward) backward = nullptr;
+    decltype(&ags_workspace_init_batch) workspace_init_batch = nullptr;
+    decltype(&ags_forward_batch) forward_batch = nullptr;
+    decltype(&ags_backward_batch) backward_batch = nullptr;
     decltype(&ags_read_status) read_status = nullptr;
     decltype(&ags_read_status_async) read_status_async = nullptr;
     decltype(&ags_error_string) error_string = nullptr;
@@ -73,13 +77,15 @@ struct Options {
     double min_headroom = 1.25;          // a pooled workspace is reused while it holds at least this many times that need
     int max_pending = 64;
     int pool_max_per_key = 16;
+    int batch_pool_max_per_key = 2;      // batch slabs hold V workspaces each: fewer of them are kept
 } opt;
 struct Counters { int64_t forward_calls = 0, status_syncs = 0, deferred_checks = 0, overflows = 0, mode_switches = 0, early_waits = 0,
-                  repaired = 0; } cnt;
+                  repaired = 0, batch_calls = 0; } cnt;
 
 using SizeKey = std::tuple<int, int, int>;           // device, h, w
 using NeedKey = std::tuple<int, int, int, int>;      // device, h, w, mode
 using PoolKey = std::tuple<int, int, int, int>;      // device, h, w, mode
+using BatchPoolKey = std::tuple<int, int, int, int, int>;   // device, h, w, mode, views
 // a pooled slab remembers the layout it was initialised for (surfels, key slots): a map that has grown or shrunk since
 // re-initialises a slab that is large enough instead of leaving one set of workspaces per map size behind
 struct Pooled { at::Tensor ws; int64_t cap; int n; };
@@ -89,6 +95,7 @@ AgsTuning tuning{};                  // kernel selection handed to the library w
 std::map<NeedKey, int64_t> need_seen;
 std::map<SizeKey, int> mode_for;
 std::map<PoolKey, std::vector<Pooled>> pool;
+std::map<BatchPoolKey, std::vector<Pooled>> batch_pool;   // slabs of `views` consecutive workspaces (rasterize_batch)
 constexpr int64_t kU32 = 0xFFFFFFFFll;
 
 struct Slot { AgsStatus* host = nullptr; hipEvent_t ev = nullptr; };
@@ -164,15 +171,18 @@ void poll_pending(bool block) {
 }
 
 // a pooled workspace laid out for n surfels with at least min_cap key slots; else a pooled slab that is large enough,
-// re-initialised for (n, cap); else a new one of cap; -> (tensor, slots, newly made or re-initialised)
-std::tuple<at::Tensor, int64_t, bool> take_workspace(const PoolKey& pk, int n, int h, int w, int64_t min_cap, int64_t cap,
-                                                    const at::TensorOptions& bytes_opt, int mode, hipStream_t stream) {
-    const size_t bytes = abi.workspace_bytes(n, h, w, cap);
+// re-initialised for (n, cap); else a new one of cap; -> (tensor, slots, newly made or re-initialised).  `views` > 1: a
+// slab of that many consecutive workspaces (ags_forward_batch's layout) from the batch pool.
+template <class Key>
+std::tuple<at::Tensor, int64_t, bool> take_workspace_from(std::map<Key, std::vector<Pooled>>& from, const Key& pk, int views, int n,
+                                                          int h, int w, int64_t min_cap, int64_t cap, const at::TensorOptions& bytes_opt,
+                                                          int mode, hipStream_t stream) {
+    const size_t bytes = (size_t)views * abi.workspace_bytes(n, h, w, cap);
     at::Tensor reuse;
     {
         std::lock_guard<std::mutex> g(mu);
-        auto it = pool.find(pk);
-        if (it != pool.end()) {
+        auto it = from.find(pk);
+        if (it != from.end()) {
             auto& v = it->second;
             for (size_t k = v.size(); k-- > 0;) {          // newest first
                 if (v[k].n == n && v[k].cap >= min_cap) {
@@ -189,8 +199,13 @@ std::tuple<at::Tensor, int64_t, bool> take_workspace(const PoolKey& pk, int n, i
     }
     at::Tensor ws = reuse.defined() ? reuse : at::empty({(int64_t)bytes}, bytes_opt);
     AgsWorkspace wss{ws.data_ptr(), (size_t)ws.numel(), cap, mode, &tuning};
-    check_rc(abi.workspace_init(&wss, n, h, w, stream), "ags_workspace_init");
+    if (views == 1) check_rc(abi.workspace_init(&wss, n, h, w, stream), "ags_workspace_init");
+    else check_rc(abi.workspace_init_batch(&wss, views, n, h, w, stream), "ags_workspace_init_batch");
     return {ws, cap, true};
+}
+std::tuple<at::Tensor, int64_t, bool> take_workspace(const PoolKey& pk, int n, int h, int w, int64_t min_cap, int64_t cap,
+                                                    const at::TensorOptions& bytes_opt, int mode, hipStream_t stream) {
+    return take_workspace_from(pool, pk, 1, n, h, w, min_cap, cap, bytes_opt, mode, stream);
 }
 
 // returns its workspace to the pool when the autograd node lets go of its saved state
@@ -205,8 +220,21 @@ struct Lease : torch::CustomClassHolder {
     }
 };
 
+// the same for a batch slab (rasterize_batch)
+struct BatchLease : torch::CustomClassHolder {
+    BatchPoolKey key; at::Tensor ws; int64_t cap; int n;
+    BatchLease(BatchPoolKey k, at::Tensor t, int64_t c, int n_) : key(k), ws(std::move(t)), cap(c), n(n_) {}
+    ~BatchLease() override {
+        std::lock_guard<std::mutex> g(mu);
+        auto& v = batch_pool[key];
+        if ((int)v.size() >= opt.batch_pool_max_per_key) v.erase(v.begin());
+        v.push_back(Pooled{std::move(ws), cap, n});
+    }
+};
+
 // (an IValue can only carry a REGISTERED custom class)
 static const auto kLeaseRegistration = torch::class_<Lease>("ags_raster", "WorkspaceLease");
+static const auto kBatchLeaseRegistration = torch::class_<BatchLease>("ags_raster", "BatchWorkspaceLease");
 
 at::Tensor f32c(const at::Tensor& t, const c10::Device& dev, const char* name) {
     at::Tensor x = t;
@@ -464,6 +492,195 @@ std::vector<at::Tensor> rasterize(const at::Tensor& means3D, const at::Tensor& m
                               render_mask, config, h, w, tanx, tany, scale_mod, weight_thres, grad_flags);
 }
 
+// ---- V views of one size and field of view as ONE autograd node (facade.SurfelRenderer.render_view_all under grad):
+// ags_forward_batch into a batch slab of V consecutive workspaces, one wait per call for the V status blocks, and
+// ags_backward_batch summing the views' gradients into one slab.  Sizing, repair and binning-mode rules are the per-view
+// node's (need_seen / mode_for are shared: a batch view needs what the same view alone needs); a truncated pass is re-run
+// before the node returns, so it never reaches autograd.
+struct RasterizeBatchFn : public torch::autograd::Function<RasterizeBatchFn> {
+    static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, const at::Tensor& means3D,
+                                                  const at::Tensor& opacities, const at::Tensor& confidences,
+                                                  const at::Tensor& colors, const at::Tensor& scales, const at::Tensor& rotations,
+                                                  const at::Tensor& bg_in, const at::Tensor& view_in, const at::Tensor& proj_in,
+                                                  const at::Tensor& mask_in, const at::Tensor& config_in, int64_t h, int64_t w,
+                                                  double tanx, double tany, double scale_mod, double weight_thres, bool want_grad) {
+        TORCH_CHECK(means3D.is_cuda(), "rasterize_batch (MI355X build): tensors must be on the GPU; there is no CPU fallback");
+        TORCH_CHECK(abi.forward_batch, "the rasterizer library is not loaded (torch_binding.init)");
+        const c10::Device dev = means3D.device();
+        const c10::DeviceGuard guard(dev);
+        collect_pending(false, false);      // sizes learnt by earlier deferred calls; their reports stay for their caller
+        hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+        const at::Tensor V = f32c(view_in, dev, "viewmatrix"), P = f32c(proj_in, dev, "projmatrix"), bg = f32c(bg_in, dev, "bg");
+        const int64_t views = V.numel() / 16;
+        TORCH_CHECK(views >= 1 && views <= 65535 && V.numel() == 16 * views && P.numel() == 16 * views,
+                    "rasterize_batch: viewmatrix / projmatrix must be (V,4,4) with 1 <= V <= 65535");
+        at::Tensor mask, cfg;
+        if (mask_in.defined() && mask_in.numel() > 0) {
+            mask = f32c(mask_in, dev, "render_mask");
+            TORCH_CHECK(mask.numel() == views * h * w, "rasterize_batch: render_mask must hold V*image_height*image_width values");
+        }
+        int flags[4] = {1, 1, 0, 0};               // normalize_depth, perpix_depth, want_stats, front_only
+        if (config_in.defined() && config_in.numel() > 0) {
+            TORCH_CHECK(config_in.numel() >= 5, "config must hold 5 values");
+            if (config_in.is_cuda()) {
+                cfg = f32c(config_in, dev, "config");
+            } else {
+                const at::Tensor c = config_in.to(at::kFloat).contiguous();
+                const float* p = c.data_ptr<float>();
+                for (int k = 0; k < 4; ++k) flags[k] = p[k + 1] > 0.f ? 1 : 0;
+            }
+        }
+        const at::Tensor m3 = f32c(means3D, dev, "means3D"), sc = f32c(scales, dev, "scales"), rot = f32c(rotations, dev, "rotations"),
+                         op = f32c(opacities, dev, "opacities").reshape({-1}), col = f32c(colors, dev, "colors_precomp"),
+                         conf = f32c(confidences, dev, "confidences").reshape({-1});
+        const int64_t n = m3.size(0);
+        TORCH_CHECK(m3.dim() == 2 && m3.size(1) == 3 && sc.numel() == 3 * n && rot.numel() == 4 * n && op.numel() == n &&
+                    col.numel() == 3 * n && conf.numel() == n, "rasterize_batch: inconsistent input shapes");
+        TORCH_CHECK(n > 0 && n <= 0x7FFFFFFF && h > 0 && w > 0, "rasterize_batch: bad sizes (a batch needs n > 0)");
+        AgsCamera cs{(int32_t)h, (int32_t)w, (float)tanx, (float)tany, (float)scale_mod, (float)weight_thres, flags[0], flags[1],
+                     flags[2], flags[3], V.data_ptr<float>(), P.data_ptr<float>(), bg.data_ptr<float>(),
+                     mask.defined() ? mask.data_ptr<float>() : nullptr, cfg.defined() ? cfg.data_ptr<float>() : nullptr};
+        AgsGaussians gs{(int32_t)n, m3.data_ptr<float>(), sc.data_ptr<float>(), rot.data_ptr<float>(), op.data_ptr<float>(),
+                        col.data_ptr<float>(), conf.data_ptr<float>(), 0, 0.01f, 0.05f};
+        const auto fo = m3.options();
+        const auto io = fo.dtype(at::kInt);
+        at::Tensor rgb = at::empty({views, 3, h, w}, fo), normal = at::empty({views, 3, h, w}, fo),
+                   depth = at::empty({views, 1, h, w}, fo), opacity = at::empty({views, 1, h, w}, fo),
+                   confidence = at::empty({views, 1, h, w}, fo), radii = at::empty({views, n}, io);
+        at::Tensor importance = cfg.defined() ? at::empty({views, n}, fo) : at::zeros({views, n}, fo);
+        at::Tensor count = cfg.defined() ? at::empty({views, n}, io) : at::zeros({views, n}, io);
+        AgsImages im{rgb.data_ptr<float>(), normal.data_ptr<float>(), depth.data_ptr<float>(), opacity.data_ptr<float>(),
+                     confidence.data_ptr<float>()};
+        AgsPerGaussian pg{importance.data_ptr<float>(), count.data_ptr<int32_t>(), radii.data_ptr<int32_t>(),
+                          AgsRowSet{nullptr, nullptr, nullptr}};
+        const SizeKey key{dev.index(), (int)h, (int)w};
+        { std::lock_guard<std::mutex> g(mu); cnt.batch_calls++; }
+        at::Tensor ws;
+        int64_t ws_cap = 0;
+        int mode = 0;
+        BatchPoolKey pk;
+        for (int attempts = 0;; ++attempts) {
+            int64_t seen;
+            {
+                std::lock_guard<std::mutex> g(mu);
+                auto mf = mode_for.find(key);
+                mode = mf == mode_for.end() ? opt.binning_mode : mf->second;
+                if (mode == AGS_BIN_RADIX) mode = AGS_BIN_TILE_SORT;    // (the batched forward bins by tile; same images)
+                auto ns = need_seen.find(NeedKey{dev.index(), (int)h, (int)w, mode});
+                seen = ns == need_seen.end() ? 0 : ns->second;
+            }
+            const int64_t floor_cap = std::max<int64_t>(1 << 16, 2 * n);
+            const int64_t min_cap = std::min(std::max<int64_t>((int64_t)(seen * opt.min_headroom) + 1024, floor_cap), kU32);
+            const int64_t new_cap = std::min(std::max<int64_t>((int64_t)(seen * opt.headroom) + 1024, floor_cap), kU32);
+            pk = BatchPoolKey{dev.index(), (int)h, (int)w, mode, (int)views};
+            std::tie(ws, ws_cap, std::ignore) = take_workspace_from(batch_pool, pk, (int)views, (int)n, (int)h, (int)w, min_cap, new_cap,
+                                                                    fo.dtype(at::kByte), mode, stream);
+            AgsWorkspace wss{ws.data_ptr(), (size_t)ws.numel(), ws_cap, mode, &tuning, nullptr, nullptr};
+            // host-side statistics flags: an abandoned pass still ADDED into importance / count - a repeat starts from zeros
+            if (!cfg.defined() && flags[2] && attempts > 0) { importance.zero_(); count.zero_(); }
+            check_rc(abi.forward_batch(&cs, (int32_t)views, &gs, &im, &pg, &wss, stream), "ags_forward_batch");
+            // the one wait of the call: the V status blocks (the first bytes of each view's workspace) in one transfer
+            const int64_t per = (int64_t)abi.workspace_bytes((int)n, (int)h, (int)w, ws_cap);
+            const at::Tensor words = ws.narrow(0, 0, views * per).view({views, per}).narrow(1, 0, (int64_t)sizeof(AgsStatus))
+                                         .contiguous().cpu();
+            const uint8_t* wb = words.data_ptr<uint8_t>();
+            std::string over;
+            int overflowed = 0;
+            bool mode_left = false;
+            {
+                std::lock_guard<std::mutex> g(mu);
+                cnt.status_syncs++;
+                for (int64_t v = 0; v < views; ++v) {
+                    AgsStatus st;
+                    std::memcpy(&st, wb + v * sizeof(AgsStatus), sizeof(AgsStatus));
+                    if ((int64_t)st.needed_instances > ws_cap) st.overflow = 1;
+                    const std::string what = note_need(key, mode, (int)n, st);
+                    if (!what.empty()) { overflowed++; if (over.empty()) over = what; }
+                }
+                if (overflowed) {
+                    cnt.overflows += overflowed;
+                    cnt.repaired++;
+                    auto mf = mode_for.find(key);
+                    int now = mf == mode_for.end() ? opt.binning_mode : mf->second;
+                    if (now == AGS_BIN_RADIX) now = AGS_BIN_TILE_SORT;
+                    mode_left = now != mode;
+                }
+            }
+            if (!overflowed) break;
+            // repaired here: the slab of the truncated pass is dropped, the batch re-runs in one of the size just learnt
+            TORCH_CHECK(attempts < 4 && (ws_cap < kU32 || mode_left), "rasterize_batch: ", over, " - more than a workspace can hold");
+        }
+        if (want_grad) {
+            ctx->save_for_backward({depth, opacity, radii, m3, sc, rot, op, col, conf, V, P, bg,
+                                    mask.defined() ? mask : at::Tensor(), cfg.defined() ? cfg : at::Tensor()});
+            ctx->saved_data["lease"] = c10::make_intrusive<BatchLease>(pk, ws, ws_cap, (int)n);
+            ctx->saved_data["scalars"] = std::vector<double>{double(h), double(w), tanx, tany, scale_mod, weight_thres,
+                                                             double(flags[0]), double(flags[1]), double(flags[2]), double(flags[3]),
+                                                             double(ws_cap), double(mode), double(views)};
+            ctx->saved_data["opac_shape"] = opacities.sizes().vec();
+        } else {
+            std::lock_guard<std::mutex> g(mu);
+            auto& v = batch_pool[pk];
+            if ((int)v.size() >= opt.batch_pool_max_per_key) v.erase(v.begin());
+            v.push_back(Pooled{ws, ws_cap, (int)n});
+        }
+        ctx->set_materialize_grads(false);
+        ctx->mark_non_differentiable({importance, count, radii});
+        return {rgb, normal, depth, opacity, confidence, importance, count, radii};
+    }
+
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list g) {
+        const auto saved = ctx->get_saved_variables();
+        const at::Tensor &depth = saved[0], &opacity = saved[1], &radii = saved[2], &m3 = saved[3], &sc = saved[4], &rot = saved[5],
+                         &op = saved[6], &col = saved[7], &conf = saved[8], &V = saved[9], &P = saved[10], &bg = saved[11],
+                         &mask = saved[12], &cfg = saved[13];
+        const std::vector<double> s = ctx->saved_data["scalars"].toDoubleVector();
+        const auto lease = ctx->saved_data["lease"].toCustomClass<BatchLease>();
+        const std::vector<int64_t> opac_shape = ctx->saved_data["opac_shape"].toIntVector();
+        const c10::Device dev = m3.device();
+        const c10::DeviceGuard guard(dev);
+        hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+        const int64_t n = m3.size(0);
+        const int32_t views = (int32_t)s[12];
+        AgsCamera cs{(int32_t)s[0], (int32_t)s[1], (float)s[2], (float)s[3], (float)s[4], (float)s[5], (int32_t)s[6], (int32_t)s[7],
+                     (int32_t)s[8], (int32_t)s[9], V.data_ptr<float>(), P.data_ptr<float>(), bg.data_ptr<float>(),
+                     mask.defined() ? mask.data_ptr<float>() : nullptr, cfg.defined() ? cfg.data_ptr<float>() : nullptr};
+        AgsGaussians gs{(int32_t)n, m3.data_ptr<float>(), sc.data_ptr<float>(), rot.data_ptr<float>(), op.data_ptr<float>(),
+                        col.data_ptr<float>(), conf.data_ptr<float>(), 0, 0.01f, 0.05f};
+        const auto fo = m3.options();
+        // the views' gradients are summed into this slab with atomics (accumulate 2): it starts from zeros
+        at::Tensor g_m = at::zeros({n, 3}, fo), g_s = at::zeros({n, 3}, fo), g_r = at::zeros({n, 4}, fo), g_o = at::zeros({n}, fo),
+                   g_c = at::zeros({n, 3}, fo);
+        at::Tensor d[5];
+        for (int k = 0; k < 5; ++k)
+            if (g[k].defined()) d[k] = f32c(g[k], dev, "image gradient");
+        auto fp = [](const at::Tensor& t) -> const float* { return t.defined() && t.numel() ? t.data_ptr<float>() : nullptr; };
+        AgsImageGrads dout{fp(d[0]), fp(d[1]), fp(d[2]), fp(d[3]), fp(d[4])};
+        AgsGaussianGrads din{};
+        din.d_means3D = g_m.data_ptr<float>(); din.d_scales = g_s.data_ptr<float>(); din.d_rotations = g_r.data_ptr<float>();
+        din.d_opacities = g_o.data_ptr<float>(); din.d_colors = g_c.data_ptr<float>(); din.d_means2D = nullptr;
+        din.accumulate = 2;
+        AgsImages im{nullptr, nullptr, depth.data_ptr<float>(), opacity.data_ptr<float>(), nullptr};
+        AgsPerGaussian pg{nullptr, nullptr, radii.data_ptr<int32_t>(), AgsRowSet{nullptr, nullptr, nullptr}};
+        AgsWorkspace wss{lease->ws.data_ptr(), (size_t)lease->ws.numel(), (int64_t)s[10], (int32_t)s[11], &tuning};
+        check_rc(abi.backward_batch(&cs, views, &gs, &im, &pg, &dout, &din, &wss, stream), "ags_backward_batch");
+        at::Tensor none;
+        return {g_m, g_o.reshape(opac_shape), none, g_c, g_s, g_r,
+                none, none, none, none, none, none, none, none, none, none, none, none};
+    }
+};
+
+std::vector<at::Tensor> rasterize_batch(const at::Tensor& means3D, const at::Tensor& opacities, const at::Tensor& confidences,
+                                        const at::Tensor& colors, const at::Tensor& scales, const at::Tensor& rotations,
+                                        const at::Tensor& bg, const at::Tensor& viewmatrix, const at::Tensor& projmatrix,
+                                        const at::Tensor& render_mask, const at::Tensor& config, int64_t h, int64_t w, double tanx,
+                                        double tany, double scale_mod, double weight_thres) {
+    const bool want_grad = at::GradMode::is_enabled() && (means3D.requires_grad() || opacities.requires_grad() ||
+                                                          colors.requires_grad() || scales.requires_grad() || rotations.requires_grad());
+    return RasterizeBatchFn::apply(means3D, opacities, confidences, colors, scales, rotations, bg, viewmatrix, projmatrix, render_mask,
+                                   config, h, w, tanx, tany, scale_mod, weight_thres, want_grad);
+}
+
 void init(const std::string& path) {
     void* hnd = dlopen(path.c_str(), RTLD_NOW | RTLD_GLOBAL);
     TORCH_CHECK(hnd, "cannot load ", path, ": ", dlerror(), " - there is no CPU fallback for the rasterizer");
@@ -473,7 +690,8 @@ void init(const std::string& path) {
     TORCH_CHECK(abi.field, path, " lacks the symbol " #name)
     AGS_SYM(workspace_bytes, ags_workspace_bytes); AGS_SYM(workspace_init, ags_workspace_init); AGS_SYM(forward, ags_forward);
     AGS_SYM(backward, ags_backward); AGS_SYM(read_status, ags_read_status); AGS_SYM(read_status_async, ags_read_status_async);
-    AGS_SYM(error_string, ags_error_string);
+    AGS_SYM(error_string, ags_error_string); AGS_SYM(workspace_init_batch, ags_workspace_init_batch);
+    AGS_SYM(forward_batch, ags_forward_batch); AGS_SYM(backward_batch, ags_backward_batch);
 #undef AGS_SYM
 }
 
@@ -511,14 +729,15 @@ std::map<std::string, int64_t> counters() {
     std::lock_guard<std::mutex> g(mu);
     return {{"forward_calls", cnt.forward_calls}, {"status_syncs", cnt.status_syncs}, {"deferred_checks", cnt.deferred_checks},
             {"overflows", cnt.overflows}, {"mode_switches", cnt.mode_switches}, {"pending", (int64_t)pending.size()},
-            {"early_waits", cnt.early_waits}, {"repaired", cnt.repaired}};
+            {"early_waits", cnt.early_waits}, {"repaired", cnt.repaired}, {"batch_calls", cnt.batch_calls}};
 }
 
 // what the module has learnt: [(device, h, w, mode, largest need seen)], [(device, h, w, mode in use)], pooled workspaces
-// [(device, h, w, mode, count, bytes)]
-std::tuple<std::vector<std::vector<int64_t>>, std::vector<std::vector<int64_t>>, std::vector<std::vector<int64_t>>> state() {
+// [(device, h, w, mode, count, bytes)], pooled batch slabs [(device, h, w, mode, views, count, bytes)]
+std::tuple<std::vector<std::vector<int64_t>>, std::vector<std::vector<int64_t>>, std::vector<std::vector<int64_t>>,
+           std::vector<std::vector<int64_t>>> state() {
     std::lock_guard<std::mutex> g(mu);
-    std::vector<std::vector<int64_t>> a, b, c;
+    std::vector<std::vector<int64_t>> a, b, c, d;
     for (auto& kv : need_seen) a.push_back({std::get<0>(kv.first), std::get<1>(kv.first), std::get<2>(kv.first), std::get<3>(kv.first), kv.second});
     for (auto& kv : mode_for) b.push_back({std::get<0>(kv.first), std::get<1>(kv.first), std::get<2>(kv.first), kv.second});
     for (auto& kv : pool) {
@@ -527,14 +746,20 @@ std::tuple<std::vector<std::vector<int64_t>>, std::vector<std::vector<int64_t>>,
         c.push_back({std::get<0>(kv.first), std::get<1>(kv.first), std::get<2>(kv.first), std::get<3>(kv.first),
                      (int64_t)kv.second.size(), bytes});
     }
-    return {a, b, c};
+    for (auto& kv : batch_pool) {
+        int64_t bytes = 0;
+        for (auto& p : kv.second) bytes += p.ws.numel();
+        d.push_back({std::get<0>(kv.first), std::get<1>(kv.first), std::get<2>(kv.first), std::get<3>(kv.first), std::get<4>(kv.first),
+                     (int64_t)kv.second.size(), bytes});
+    }
+    return {a, b, c, d};
 }
 
 // forget everything learnt (sizes, modes, pooled workspaces); pending checks are settled first (errors swallowed)
 void reset_state() {
     try { poll_pending(true); } catch (...) {}
     std::lock_guard<std::mutex> g(mu);
-    need_seen.clear(); mode_for.clear(); pool.clear(); overflow_reports.clear();
+    need_seen.clear(); mode_for.clear(); pool.clear(); batch_pool.clear(); overflow_reports.clear();
 }
 
 }  // namespace
@@ -543,6 +768,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "native host side of diff_gaussian_rasterization_2d (MI355X build): autograd node over the C ABI of libags_raster.so";
     m.def("init", &init, "load the rasterizer library (path) and resolve the C ABI");
     m.def("rasterize", &rasterize);
+    m.def("rasterize_batch", &rasterize_batch, "V views of one size and field of view as one autograd node (ags_forward_batch / "
+          "ags_backward_batch), checked and repaired before it returns");
     m.def("check_overflow", []() { poll_pending(true); },
           "wait for the status copies of all forward passes issued so far; raises if one of them outgrew its workspace");
     m.def("settle", []() { return collect_pending(true); },

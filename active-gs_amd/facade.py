@@ -66,6 +66,41 @@ class _FacadePost(torch.autograd.Function):
         return d_nr, d_depth, None, None, None
 
 
+class _FacadePostBatch(torch.autograd.Function):
+    """_FacadePost for ``V`` views of one size and field of view: ``(V,C,H,W)`` batches in, one launch forward
+    (``ags_facade_post_batch``), one backward (``ags_facade_post_backward_batch``); per view the same arithmetic."""
+
+    @staticmethod
+    def forward(ctx, normal_raw, depth, opacity, tanx, tany):
+        from . import _lib
+        from ._lib import ptr
+        V, _, H, W = depth.shape
+        depth_c, op_c = depth.detach().float().contiguous(), opacity.detach().float().contiguous()
+        nr_c = normal_raw.detach().float().contiguous()
+        d2n = torch.empty(V, 3, H, W, device=depth.device, dtype=torch.float32)
+        n_out = torch.empty_like(d2n)
+        _lib.check(_lib.load().ags_facade_post_batch(V, H, W, float(tanx), float(tany), ptr(nr_c), ptr(depth_c), ptr(op_c),
+                                                     ptr(n_out), ptr(d2n), _lib.current_stream()), "ags_facade_post_batch")
+        ctx.save_for_backward(depth_c, op_c, nr_c)
+        ctx.geom = (V, H, W, float(tanx), float(tany))
+        return n_out, d2n
+
+    @staticmethod
+    def backward(ctx, g_n, g_d):
+        from . import _lib
+        from ._lib import ptr
+        V, H, W, tanx, tany = ctx.geom
+        depth_c, op_c, nr_c = ctx.saved_tensors
+        g_n = None if g_n is None else g_n.float().contiguous()
+        g_d = None if g_d is None else g_d.float().contiguous()
+        d_nr = torch.empty_like(nr_c) if ctx.needs_input_grad[0] else None
+        d_depth = torch.zeros(V, 1, H, W, device=depth_c.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.load().ags_facade_post_backward_batch(V, H, W, tanx, tany, ptr(nr_c), ptr(depth_c), ptr(op_c), ptr(g_n),
+                                                              ptr(g_d if d_depth is not None else None), ptr(d_nr), ptr(d_depth),
+                                                              _lib.current_stream()), "ags_facade_post_backward_batch")
+        return d_nr, d_depth, None, None, None
+
+
 def depth_to_normal(depth: torch.Tensor, mask: torch.Tensor, fov) -> torch.Tensor:
     """(1,H,W) depth, (1,H,W) bool mask -> (3,H,W) unit normals from the four neighbouring
     back-projected points.  Quirk kept from the reference: the x focal is derived from
@@ -175,10 +210,18 @@ class SurfelRenderer:
     * passes WITHOUT grad (planners, evaluation, mesh, GUI, the count render of post-processing) of a renderer whose views
       share one field of view are rendered as one batch the first time one of them is asked for (``ViewBatch``:
       blockIdx.y = view) and served from it afterwards; ``update_attr`` forgets the batch;
-    * passes WITH grad go view by view through the drop-in module with its workspace checks deferred to ONE wait per
-      batch of views (``rasterizer.deferred_status``); a view that outgrew its workspace makes the loop run again with
-      the size just learnt - the caller never sees truncated tile lists or an exception.
-    A module injected by the caller (``rasterizer_module``: the CPU tests' adapter over the oracle) takes neither path."""
+    * ``render_view_all(require_grad=True)`` of such a renderer (the training renders, gaussian_map.py:94-104) is ONE
+      autograd node per chunk of views (``rasterizer.rasterize_batch``: ags_forward_batch / ags_backward_batch, checked
+      and repaired before it returns) and one post-processing node per chunk (``_FacadePostBatch``); the chunks are those
+      of the passes without grad (BATCH_BYTES_BUDGET).  ``GRAD_BATCH = False`` (class or instance) keeps the view loop;
+    * other passes WITH grad (``render_view(i, require_grad=True)``, differing fields of view, one view) go view by view
+      through the drop-in module with its workspace checks deferred to ONE wait per batch of views
+      (``rasterizer.deferred_status``); a view that outgrew its workspace makes the loop run again with the size just
+      learnt - the caller never sees truncated tile lists or an exception.
+    A module injected by the caller (``rasterizer_module``: the CPU tests' adapter over the oracle) takes none of the
+    batched paths."""
+
+    GRAD_BATCH = True
 
     def __init__(self, extrinsics, intrinsics, gaussians_attr, background_color, near_far, resolution, device,
                  render_masks=None, rasterizer_module=None):
@@ -353,7 +396,46 @@ class SurfelRenderer:
                 radii_sum = radii_sum + out[8].to(radii_sum.device)
         return per_view, radii_sum
 
+    def _render_grad_batch(self, require_importance, front_only):
+        """All views under grad: one ``rasterize_batch`` node and one ``_FacadePostBatch`` node per chunk of views; returns
+        the 9-tuple of ``render_view_all``."""
+        from . import raster_api as api
+        from .rasterizer import rasterize_batch, state
+        dev = self.gaussian_means.device
+        n, V, h, w = len(self.gaussian_means), self.batch_size, self.h, self.w
+        key = (bool(require_importance), bool(front_only))
+        if key not in self._configs:
+            self._configs[key] = torch.tensor([1.0, 1.0, 1.0, 1.0 if require_importance else 0.0,
+                                               1.0 if front_only else 0.0]).to(dev)
+        masks = None
+        if self._has_masks:
+            masks = (torch.stack([m.to(dev).reshape(h, w) for m in self.render_masks]) if not torch.is_tensor(self.render_masks)
+                     else self.render_masks.to(dev).reshape(V, h, w))
+        tanx, tany = self._tan_host[0]
+        # views per node: the workspaces of a chunk stay below BATCH_BYTES_BUDGET (sized like the binding sizes them:
+        # twice the largest need seen for this view size)
+        cap = max(1 << 16, 2 * n)
+        if V * api.workspace_bytes(n, h, w, cap) > BATCH_BYTES_BUDGET:
+            seen = [v for k, v in state()["need_seen"].items() if k[:3] == (dev.index, h, w)]
+            cap = max([cap] + [2 * v + 1024 for v in seen])
+        CH = int(max(1, min(V, 65535, BATCH_BYTES_BUDGET // max(api.workspace_bytes(n, h, w, cap), 1))))
+        chunks = []
+        with torch.enable_grad():
+            for v0 in range(0, V, CH):
+                v1 = min(V, v0 + CH)
+                rgb, normal, depth, opacity, confidence, importance, count, radii = rasterize_batch(
+                    self.gaussian_means, self.gaussian_opacities, self.gaussian_confidences, self.gaussian_harmonics[:, 0, :],
+                    self.gaussian_scales, self.gaussian_rotations, self.background_color, self.view_matrices[v0:v1],
+                    self.projection_matrices[v0:v1], h, w, tanx, tany, render_masks=None if masks is None else masks[v0:v1],
+                    config=self._configs[key])
+                normal, d2n = _FacadePostBatch.apply(normal, depth, opacity, tanx, tany)
+                chunks.append((rgb, depth, normal, opacity, d2n, confidence, importance, count, radii))
+        out = chunks[0] if len(chunks) == 1 else tuple(torch.cat(c, 0) for c in zip(*chunks))
+        return out[:8] + (out[8].sum(0, dtype=torch.int32) > 0,)
+
     def render_view_all(self, require_grad=False, require_importance=False, front_only=False):
+        if require_grad and self.GRAD_BATCH and self._batchable():
+            return self._render_grad_batch(require_importance, front_only)
         if not require_grad and self._batchable():
             with torch.no_grad():
                 per_view = [self._batched_view(i, require_importance, front_only) for i in range(self.batch_size)]

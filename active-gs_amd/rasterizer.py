@@ -121,14 +121,18 @@ def get_option(name: str) -> float:
 
 
 def counters() -> dict:
-    """forward_calls, status_syncs (calls that read the status block back), deferred_checks, overflows, mode_switches."""
+    """forward_calls, status_syncs (calls that read the status block back), deferred_checks, overflows, mode_switches,
+    batch_calls (rasterize_batch calls; they do not count as forward_calls)."""
     return dict(_load_binding().counters())
 
 
 def state() -> dict:
-    need, modes, pooled = _load_binding().state()
+    """need_seen {(device, h, w, mode): need}, mode_for {(device, h, w): mode}, pooled {(device, h, w, mode): count/bytes}
+    and batch_pooled {(device, h, w, mode, views): count/bytes} (rasterize_batch's slabs)."""
+    need, modes, pooled, batch_pooled = _load_binding().state()
     return dict(need_seen={tuple(r[:4]): r[4] for r in need}, mode_for={tuple(r[:3]): r[3] for r in modes},
-                pooled={tuple(r[:4]): dict(count=r[4], bytes=r[5]) for r in pooled})
+                pooled={tuple(r[:4]): dict(count=r[4], bytes=r[5]) for r in pooled},
+                batch_pooled={tuple(r[:5]): dict(count=r[5], bytes=r[6]) for r in batch_pooled})
 
 
 def reset_state() -> None:
@@ -234,3 +238,20 @@ class GaussianRasterizer(nn.Module):
 
     # (nn.Module.__call__ goes through the hook machinery: ~3 us per call that this module has no use for)
     __call__ = forward
+
+
+def rasterize_batch(means3D, opacities, confidences, colors, scales, rotations, bg, viewmatrices, projmatrices, h, w, tanfovx,
+                    tanfovy, render_masks=None, config=None, scale_modifier=1.0, weight_thres=0.03):
+    """``V`` views of one size and field of view as ONE autograd node (csrc/torch_binding.cpp: RasterizeBatchFn):
+    ``viewmatrices`` / ``projmatrices`` ``(V,4,4)``, ``render_masks`` ``(V,H,W)`` or None, ``config`` as the module's
+    setting.  Returns ``(rgb, normal, depth, opacity, confidence)`` as ``(V,C,H,W)`` batches and ``importance, count,
+    radii`` as ``(V,n)`` - per view what ``GaussianRasterizer`` returns for it, bit for bit.  The pass is checked and
+    repaired before the call returns (one wait for the V status blocks); its backward sums the views' gradients into one
+    slab (gradients for means3D, opacities, colors, scales and rotations)."""
+    if not means3D.is_cuda:
+        raise RuntimeError("rasterize_batch (MI355X build): tensors must be on the GPU; there is no CPU fallback")
+    b = _binding or _load_binding()
+    none = _empty(means3D.device)
+    return tuple(b.rasterize_batch(means3D, opacities, confidences, colors, scales, rotations, bg, viewmatrices, projmatrices,
+                                   none if render_masks is None else render_masks, none if config is None else config,
+                                   int(h), int(w), float(tanfovx), float(tanfovy), float(scale_modifier), float(weight_thres)))

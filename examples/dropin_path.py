@@ -6,7 +6,11 @@
 
 Timed: one training-iteration's worth of renders + backward, (a) BASELINE config C2 (200 k surfels, one 1200x680 view)
 and (b) the reference's own shape (8 views @512x512, incremental.yaml:24-25, habitat.yaml:8-9), against the fused
-trainer path (``SurfelTrainer`` / C ABI, no autograd, no per-call allocation) on the same views."""
+trainer path (``SurfelTrainer`` / C ABI, no autograd, no per-call allocation) on the same views.
+
+By default ``render_view_all(require_grad=True)`` of several views of one field of view is one autograd node per batch
+of views (``SurfelRenderer.GRAD_BATCH``); ``--per-view`` switches that off (one module call per view, as before) for
+the A/B.  C2 has one view: it takes the per-view path either way."""
 import argparse
 import json
 import os
@@ -111,7 +115,7 @@ def run(tag, n, h, w, views, iters, focal=None):
         tr.step(cams, fn, cap)
     torch.cuda.synchronize()
     t_fused = (time.perf_counter() - t0) / iters
-    return dict(config=tag, surfels=n, image=[h, w], views=views, iterations=iters,
+    return dict(config=tag, grad_batch=SurfelRenderer.GRAD_BATCH, surfels=n, image=[h, w], views=views, iterations=iters,
                 dropin_facade_ms_per_iteration=round(t_mod * 1e3, 3), dropin_facade_ms_per_view=round(t_mod * 1e3 / views, 3),
                 module_only_ms_per_iteration=round(t_only * 1e3, 3), module_only_ms_per_view=round(t_only * 1e3 / views, 3),
                 fused_trainer_eager_ms_per_iteration=round(t_fused * 1e3, 3),
@@ -123,7 +127,10 @@ def run(tag, n, h, w, views, iters, focal=None):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--per-view", action="store_true",
+                    help="render_view_all under grad view by view (SurfelRenderer.GRAD_BATCH = False) instead of one batch node")
     a = ap.parse_args()
+    SurfelRenderer.GRAD_BATCH = not a.per_view
     out = [run("C2: 200k surfels, one 1200x680 view", 200_000, 680, 1200, 1, a.iters),
            run("reference shape: 200k surfels, 8 views @512x512 (60 deg)", 200_000, 512, 512, 8, a.iters, focal=0.5 * 512 / 0.57735)]
     for o in out:

@@ -550,6 +550,12 @@ int ags_facade_post_batch(int32_t views, int32_t h, int32_t w, float tanfov_x, f
 int ags_facade_post_backward(int32_t h, int32_t w, float tanfov_x, float tanfov_y, const float* normal_raw,
                              const float* depth, const float* opacity, const float* g_normal, const float* g_d2n,
                              float* d_normal_raw, float* d_depth, ags_stream_t stream);
+/* The backward of ags_facade_post_batch in one launch: `views` views of one size and field of view, every image argument
+ * a contiguous (views,C,H,W) batch; per view the arithmetic of ags_facade_post_backward (d_depth, (views,1,H,W), is ADDED
+ * to with atomics - zero it first; g_normal / g_d2n NULL = zero for every view). */
+int ags_facade_post_backward_batch(int32_t views, int32_t h, int32_t w, float tanfov_x, float tanfov_y, const float* normal_raw,
+                                   const float* depth, const float* opacity, const float* g_normal, const float* g_d2n,
+                                   float* d_normal_raw, float* d_depth, ags_stream_t stream);
 
 /* ---- Map growth and pruning (replaces the torch/cv2 code of GaussianMap.add_gaussians, cal_mask,
  * prune and voxel_downsample: /root/reference/mapping/gaussian_map.py:234-246,294-489,
